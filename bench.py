@@ -15,7 +15,7 @@ The pair count grows with the square of the collection while the work (bases see
 screens a share of the rows on every rank, assigns the candidate pairs to ranks cluster by cluster (balanced, order-independent), moves
 exactly the sketches that are needed point-to-point and gathers the results.  value = N_total (N_total - 1) / 2 / step time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (seeding kernel, HBM bound per SURVEY 8d: 0.354 algorithmic
+Prints ONE compact JSON line on rank 0 (contract in the task statement; LINE_FIELDS); `--detail FILE` writes the full record, with `roofline` (seeding kernel, HBM bound per SURVEY 8d: 0.354 algorithmic
 bytes/base; plus the VALU issue fraction that actually binds it) and `cpu_baseline` (the C++ oracle = a port of the reference algorithms,
 run on this box's host cores on the same, full workload at several thread counts -- about 20 s in all; the best point is the value; the Rust
 reference cannot be built here).
@@ -587,10 +587,60 @@ def stage_rooflines(tm, steps, units, c, m, pairs_chained, sp):
     return rows
 
 
-def run_triangle(args, torch, dist, sk, ctx, comm, transport, rank, world, device, n_local, order, strong, steps, warmup, want_cpu, want_e2e, defer_cpu_legs=False):
+# the result line on stdout: the headline and the few figures that compare across runs, small enough to survive a capture of the output's tail.
+# Everything else (per-stage rooflines, units, variants, the oracle's thread sweep, notes) is in the full record, which --detail FILE writes.
+LINE_FIELDS = (("metric", None), ("value", None), ("unit", None), ("n_gpus", None), ("steps", None), ("warmup", None), ("ms_per_step", None),
+               ("ms_per_step_median_rank0", None), ("higher_is_better", None), ("scaling", None), ("vs_baseline", None),
+               ("dtype", None), ("data", None),
+               ("config", ("workload", "genomes", "genomes_per_gpu", "pairs", "chained_pairs", "kept_pairs", "order", "transport", "db_genomes", "queries", "hits",
+                           "hits_in_own_clade", "library_live_gb")),
+               ("phase_ms_per_step", None), ("bases_per_s_per_gpu", None), ("chained_pairs_per_s_per_gpu", None), ("genomes_per_s_per_gpu", None),
+               ("roofline", ("kernel", "stage", "bound", "achieved", "peak", "unit", "frac", "frac_hip_events", "valu_frac")),
+               ("roofline_chain", ("achieved", "frac", "traffic_over_algorithmic")),
+               ("cpu_baseline", ("value", "unit", "kind", "cores", "cpus_granted", "chained_pairs_per_s", "delta_vs_oracle", "error")),
+               ("strong", ("ms_per_step", "value", "steps", "collection", "genomes_per_gpu", "chained_pairs")),
+               ("e2e", ("wall_s", "pairs_per_s", "gpus", "error")))
+
+
+def emit(out, detail):
+    """Prints the result line (LINE_FIELDS of the record, error texts cut to 300 characters); with `detail`, first writes the whole record there and names
+    it in the line."""
+    line = {}
+    for k, sub in LINE_FIELDS:
+        if k in out:
+            v = out[k]
+            line[k] = {x: str(v[x])[:300] if x == "error" else v[x] for x in sub if x in v} if sub and isinstance(v, dict) else v
+    if detail:
+        with open(detail, "w") as f:
+            json.dump(out, f)
+        line["detail"] = detail
+    print(json.dumps(line), flush=True)
+
+
+DUMP_LIMIT = 60_000_000                    # --dump-outputs: bytes of column data at most (under 64 MB with the .npy headers)
+
+
+def dump_rows(d, a_name, a, b_name, b, res):
+    """--dump-outputs: the result rows a step returned, one DIR/<name>.npy per column (the two genome indices in float64, the result's float32 fields
+    as float32, its integer fields in float64), rows sorted by (a, b) so that two builds compare row by row whatever order the rows came in.  Beyond
+    DUMP_LIMIT bytes a fixed, seeded sample of the sorted rows is written (`row` = their positions in the sorted order)."""
+    os.makedirs(d, exist_ok=True)
+    order = np.lexsort((b, a))
+    cols = [(a_name, a), (b_name, b)] + [(f, res[f]) for f in res.dtype.names]
+    row_bytes = sum(4 if c.dtype == np.float32 else 8 for _, c in cols)
+    if len(order) * row_bytes > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(SEED0).choice(len(order), DUMP_LIMIT // (row_bytes + 8), replace=False))   # (+ 8: the `row` column)
+        np.save(os.path.join(d, "row.npy"), keep.astype(np.float64))
+        order = order[keep]
+    for name, c in cols:
+        np.save(os.path.join(d, name + ".npy"), c[order].astype(np.float32 if c.dtype == np.float32 else np.float64))
+
+
+def run_triangle(args, torch, dist, sk, ctx, comm, transport, rank, world, device, n_local, order, strong, steps, warmup, want_cpu, want_e2e, defer_cpu_legs=False, dump_dir=None):
     """One measured triangle workload: every rank makes its n_local genomes of the collection (n_local * world, in `order`), W warm-up steps, `steps` timed steps
     between barriers, the MAX over ranks.  Rank 0 returns the bench line (a dict), the others None.  want_cpu: the oracle beside it (`cpu_baseline`, rank 0 only:
-    on the genomes rank 0 holds when that is the whole workload, else on whole clades sampled from the collection, which rank 0 generates for itself)."""
+    on the genomes rank 0 holds when that is the whole workload, else on whole clades sampled from the collection, which rank 0 generates for itself).
+    dump_dir: rank 0 writes the rows of the last timed step there (dump_rows)."""
     n_total = n_local * world
     assert n_total % CLADE == 0, "the collection must consist of whole clades"
     canon = genome_order(n_total, order)                               # global genome index -> canonical id
@@ -667,6 +717,9 @@ def run_triangle(args, torch, dist, sk, ctx, comm, transport, rank, world, devic
         dist.barrier()
     dt = time.perf_counter() - t0
     tm = ctx.timings()
+    if dump_dir and rank == 0:
+        i, j, res = last["result"]
+        dump_rows(dump_dir, "i", i, "j", j, res)
     units = None
     if comm is None and not args.no_units:
         # what the step worked on, counted once OUTSIDE the timed region (a sketch + screen + chaining call with per-pair stage statistics): the units roofline_stages prices
@@ -879,7 +932,12 @@ def main():
                     "else 0 = none")
     ap.add_argument("--strong-steps", type=int, default=4)
     ap.add_argument("--rows-everywhere", action="store_true", help="several GPUs: gather the result rows on every rank (skh_triangle_distributed) instead of on rank 0 (SKH_DIST_ROWS_TO_ROOT)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the result rows of the last one as DIR/<column>.npy (float32 / float64; "
+                    "rows sorted by genome pair; a seeded sample beyond %d bytes): two builds compare output for output" % DUMP_LIMIT)
+    ap.add_argument("--detail", default="", metavar="FILE", help="write the full record (every block the result line leaves out) to FILE as JSON")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -908,7 +966,10 @@ def main():
             raise SystemExit("the search workload is single-GPU")
         if args.c == 125:
             args.c = C = 70            # --medium, BASELINE config 5
-        print(json.dumps(run_search(args, torch, sk, ctx, device)[0]))
+        line, (q, r, res, _) = run_search(args, torch, sk, ctx, device)
+        if args.dump_outputs:
+            dump_rows(args.dump_outputs, "query", q, "ref", r, res)
+        emit(line, args.detail)
         return
 
     strong = args.collection > 0
@@ -954,7 +1015,7 @@ def main():
         real = {"root": os.path.basename(args.root_fasta), "root_bases": len(seq),
                 "generator": "every genome = the root with substitution rate U(0.005, 0.08), 0-5 deletions of 10-50 kb, cut into 1-20 contigs (make_genomes; the point-substitution model of tests/helpers.mutate)"}
     out = run_triangle(args, torch, dist, sk, ctx, comm, transport, rank, world, device, n_local, order, strong, args.steps, args.warmup,
-                       want_cpu=True, want_e2e=not args.no_e2e and not strong and not args.root_fasta, defer_cpu_legs=True)
+                       want_cpu=True, want_e2e=not args.no_e2e and not strong and not args.root_fasta, defer_cpu_legs=True, dump_dir=args.dump_outputs)
     if real is not None and rank == 0:
         # what a real genome puts on the timed path that i.i.d. sequence does not: seeds with several positions (list storage) and seeds beyond the band (dropped by the join, chain.rs:674-696)
         b0, co0, cg0, ng0, _ = make_genomes(torch, device, [0], mean_len=args.mean_len, members=CLADE)
@@ -1011,7 +1072,7 @@ def main():
         out["variants"] = variants
     if rank == 0:
         out.pop("_cpu_legs")()                                         # (cpu_baseline, e2e: behind every GPU measurement, see run_triangle)
-        print(json.dumps(out))
+        emit(out, args.detail)
     if comm is not None:
         comm.close()
     if dist.is_initialized():

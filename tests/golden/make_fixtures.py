@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ from the reference checkout (run in the build container only).
+"""Regenerate tests/golden/ from the reference checkout: `make_fixtures.py <reference checkout>`.
 
 Fixtures are DATA the reference's own tests hold (test_files/*), never reference source:
   * o157_plasmid.fasta, viruses.fna, all_ns.fa, empty_fasta.fa, test.fasta, e.coli-W.fasta.gz
-    -> byte copies of /root/reference/test_files/<name>
+    -> byte copies of test_files/<name> of the reference checkout
   * o157_sketch.npz -> compact re-encoding of test_files/e.coli-o157.fasta.sketch
     (pre-0.3 bincode layout): sorted (seed,pos,ctg<<1|canon) u32 triples,
     sorted u64 markers, contig lengths, contig names, c, k, total length.
@@ -11,12 +11,12 @@ Fixtures are DATA the reference's own tests hold (test_files/*), never reference
     (search --median, learned ANI off) and the range assertions of tests/tests.rs,
     tests/int_test_new.rs.
 
-/root/reference does not exist on the GPU box, hence the committed copies.
+The tests do not need the reference checkout, hence the committed copies.
 """
 import json, os, shutil, struct, sys
 import numpy as np
 
-REF = "/root/reference/test_files"
+REF = os.path.join(sys.argv[1] if len(sys.argv) > 1 else "reference", "test_files")
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 

@@ -39,3 +39,22 @@ def test_the_profile_is_refused_for_other_sources_or_workloads(monkeypatch):
     monkeypatch.setattr(bench, "kernel_sources_sha", lambda: "0" * 16)
     sp, note = bench.load_stage_profile(True)
     assert sp is None and "other kernel sources" in note
+
+
+def test_the_result_line_stays_small_and_the_detail_keeps_everything(tmp_path, capsys):
+    """The line on stdout must survive a capture of the output's tail: a worst case (the committed default line with long error texts, many steps and
+    every block) stays under 4,000 bytes, keeps the headline, and --detail writes the whole record."""
+    rec = json.loads(open(os.path.join(ROOT, "profiles", "r06_bench.json")).read().strip().splitlines()[-1])
+    rec["steps"] = 1000; rec["step_wall_ms_rank0"] = [12.345678] * 1000
+    rec["cpu_baseline"]["error"] = "x" * 5000; rec["e2e"] = {"error": "y" * 5000}
+    rec["per_rank"] = {"chained_pairs": [11875] * 8}
+    detail = str(tmp_path / "detail.json")
+    bench.emit(rec, detail)
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 4000
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "phase_ms_per_step"):
+        assert line[k] == rec[k]
+    assert line["config"]["chained_pairs"] == rec["config"]["chained_pairs"] and line["roofline"]["frac"] == rec["roofline"]["frac"]
+    assert line["cpu_baseline"]["value"] == rec["cpu_baseline"]["value"] and line["strong"]["ms_per_step"] == rec["strong"]["ms_per_step"]
+    assert line["detail"] == detail and json.load(open(detail)) == rec

@@ -2,9 +2,9 @@
 """Convert the learned-ANI regression model parameters into a flat binary table.
 
 The reference embeds two trained gradient-boosted-tree models as JSON text
-(/root/reference/src/model.rs:2 = c125 model, :5 = c200 model; consumed by regression.rs:12-28).
+(src/model.rs:2 of the reference checkout = c125 model, :5 = c200 model; consumed by regression.rs:12-28).
 The numbers are trained *weights* (data), needed for output parity because learned ANI is
-default-on at c >= 70 (parse.rs:885-889).  This script (run in the build container only) parses
+default-on at c >= 70 (parse.rs:885-889).  This script (`extract_gbdt_model.py <reference checkout>`) parses
 the JSON and writes, per model, skani_amd/data/gbdt_c{125,200}.bin:
 
     u32 magic 'GBDT' | u32 n_trees | u32 n_features | f32 shrinkage | f32 bias | u32 n_nodes_total
@@ -17,7 +17,7 @@ f32 values are obtained the way serde_json fills an f32 field: decimal -> f64 ->
 import json, os, re, struct, sys
 import numpy as np
 
-SRC = "/root/reference/src/model.rs"
+SRC = os.path.join(sys.argv[1] if len(sys.argv) > 1 else "reference", "src", "model.rs")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "skani_amd", "data")
 
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root; through gpurun): tools/gpu_job.sh <tag> <section> [<section> ...]
 # One parameterised job instead of a script per GPU run.  Everything lands in gpurun_out/ under names that carry <tag>.
-# sections: suite | suite:<pytest -k expr> | smoke | bench | benchquick | trace | gaps | pmc | traffic | forcedist | config4 | config4dist | touch | ranks8 | search | search113k | presets | fuzz[:rounds] | mergejoin | wide | predict | cli | sortab | skeysavg | alloctrace | config4trace | hosttrace | screenab | overlap | probe | stageprofile | realdense | densetraces | variants (after bench) | benchmini (first: stops the job when bench.py fails)
+# sections: suite | suite:<pytest -k expr> | smoke | bench | benchquick | trace | gaps | pmc | traffic | forcedist | config4 | config4dist | touch | search | search113k | presets | fuzz[:rounds] | mergejoin | wide | predict | cli | sortab | skeysavg | alloctrace | config4trace | hosttrace | screenab | overlap | probe | stageprofile | realdense | densetraces | variants (after bench) | benchmini (first: stops the job when bench.py fails)
 mkdir -p gpurun_out
 tag=$1; shift
 short() { python - "$1" <<'PY'
@@ -37,8 +37,6 @@ import json; d=json.load(open('gpurun_out/bench_$tag.json')); r=d['roofline']; p
                  short gpurun_out/${tag}_config4_dist_w1.json
                  SKH_TUNE_DIST_KEY_RANGE_W1=1 SKH_TRACE=1 timeout 600 python bench.py --force-dist --no-e2e --cpu-clades 0 --collection 10000 --steps 1 --warmup 2 2>&1 >/dev/null | grep "skh trace\] dist" | tail -12 ;;
     touch) for t in 0 1; do SKH_TUNE_ALLOC_TOUCH=$t timeout 900 python bench.py --collection 10000 --steps 7 --warmup 1 --cpu-clades 0 --no-e2e > gpurun_out/${tag}_touch$t.json 2> gpurun_out/${tag}_touch$t.err || tail -3 gpurun_out/${tag}_touch$t.err; short gpurun_out/${tag}_touch$t.json; done ;;
-    ranks8) timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --one-device --steps 3 --warmup 1 --cpu-sample-clades 5 > gpurun_out/${tag}_8ranks.json 2> gpurun_out/${tag}_8ranks.err || tail -5 gpurun_out/${tag}_8ranks.err
-            short gpurun_out/${tag}_8ranks.json ;;
     search) timeout 1200 python bench.py --workload search --db-genomes 65000 --queries 1000 --steps 3 --warmup 1 > gpurun_out/${tag}_search_65k.json 2> gpurun_out/${tag}_search_65k.err && short gpurun_out/${tag}_search_65k.json || tail -5 gpurun_out/${tag}_search_65k.err
             python -c "
 import json; d=json.load(open('gpurun_out/${tag}_search_65k.json')); print(json.dumps(d['roofline'])[:600]); print(json.dumps(d['cpu_baseline'])[:1500])" ;;
